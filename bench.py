@@ -13,7 +13,16 @@ buckets) overlapped with the reference's Adam step (scene/gaussian_model.py:
 arrives.  Inputs live in HBM before the timed region.  ``value`` = views
 processed by all ranks / max-over-ranks wall time of the K timed steps.
 
-Also reported (rank 0): fwd+bwd ms/view (hipEvents, median over >= 100 views,
+A plain run sets up, warms up, times the K steps and prints the line: ``value``, ``ms_per_step`` (the milliseconds one
+timed step took) and the configuration.  ``--dump-outputs DIR`` then calls the timed path once more, untimed, from the
+state the first timed step started from (the restored initial parameters and optimizer state) and writes what that
+call returned (image, radii, dL/dmeans2D, num_rendered, loss) and the first Adam moment it left for every trained
+parameter as DIR/<name>.npy (float32; arrays above a size cap as a fixed seeded sample, 64 MB in all).  The scene,
+camera, target and network are seeded, so the call's inputs are identical in every run and two runs agree to the
+rounding of the backward's float-atomic gradient sums; the state after the K timed steps does not (Adam turns the sign
+of a cancelling sum into a whole +-lr move, which compounds: 1e-2 in the image after 25 steps), so it is not written.
+
+``--full`` also reports (rank 0): fwd+bwd ms/view (hipEvents, median over >= 100 views,
 SURVEY.md 8(d)); per-kernel device times (hipEvents around each launch inside
 the C-ABI, from a separate pass so they do not perturb the timed steps); the
 roofline of the dominant kernel -- its binding roof from the committed PMC pass
@@ -29,7 +38,8 @@ which the reference runs every iteration below densify_until_iter); configuratio
 offset-norm term of the loss (train.py:329-332) and the network's Adam group (training_setup :843, the offset
 schedule's rate at that iteration).  A separate line (config.workload says "MLP live"); the headline is without.
 
-  python bench.py [--gpus N --steps K --warmup W --config 4 --cpu-baseline auto|off --with-mlp]
+  python bench.py [--gpus N --steps K --warmup W --config 4 --with-mlp --dump-outputs DIR]
+  python bench.py --full [... --cpu-baseline auto|off]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 ``--gpus N`` means N ranks: without a launcher (no WORLD_SIZE in the environment) and N > 1, this process
@@ -334,6 +344,36 @@ def cpu_baseline(cfg, seed, min_seconds=10.0, max_views=64):
                       f"OpenMP C oracle on {threads} threads ({model}): {dt:.1f} s"}
 
 
+# --dump-outputs: 64 MB in all.  The image is written whole up to 1920x1080 (24.9 MB); every other array, and a
+# larger image, as a fixed seeded sample of its elements (at most a dozen arrays of 3 MB each)
+DUMP_IMAGE_ELEMS = 6_500_000
+DUMP_ARRAY_ELEMS = 750_000
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, arrays):
+    """Write ``arrays`` (name -> tensor or number) as ``directory/<name>.npy``, float32.  An array with more
+    elements than its cap is reduced to a sample of its flattened elements at sorted indices drawn from a generator
+    seeded by the array's size alone, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        # a number (a count can pass float32's 2^24) as one float64
+        a = a.detach().to(torch.float32) if torch.is_tensor(a) else torch.tensor([float(a)], dtype=torch.float64)
+        cap = DUMP_IMAGE_ELEMS if name == "render" else DUMP_ARRAY_ELEMS
+        if a.numel() > cap:
+            idx = np.sort(np.random.default_rng(a.numel()).integers(0, a.numel(), size=cap))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        a = a.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes at '{name}'")
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
         sk.bind(("127.0.0.1", 0))
@@ -374,7 +414,15 @@ def main():
                     help="densify_and_prune every N steps (train.py:610-648); default 100 for config 5, else off")
     ap.add_argument("--with-mlp", action="store_true",
                     help="DirectTemporalNeRF live in the step (iteration 5000): offsets, offset-norm loss, its Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the drop-in API's step, fwd+bwd ms/view, the data-parallel "
+                         "exchange and replica check, per-kernel times with the roofline, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, one more call of the timed path from the restored initial state; what it "
+                         "returned and its Adam first moments go to DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     err = check_ranks(args.gpus)
     if err:
         print(f"bench.py: {err}", file=sys.stderr)
@@ -427,6 +475,7 @@ def main():
     from gsd_amd.densify import GaussianDensifier
     dens = GaussianDensifier(pc, opt)   # the statistics run every step; densify_and_prune every densify_every
     nstep = [0]
+    last_loss = [None]
 
     # autograd's seed gradient d loss / d loss = 1, allocated once (a bare loss.backward() launches a fill each
     # step; identical semantics)
@@ -435,7 +484,7 @@ def main():
     # The step as one native call (gsd_amd.train_step.FusedTrainStep: the drop-in path's kernels with the same
     # arguments, its argument structures built once) where it applies -- one rank, no offsets / SE(3) -- so the host
     # does not pace small views; GSD_TRAIN_STEP=0 times the drop-in API path (render + training_loss +
-    # step_in_backward + add_densification_stats) instead.  Both are timed below (value: the former).
+    # step_in_backward + add_densification_stats) instead.  --full times both (value: the former).
     fused_step = None
     if FUSED_STEP and world == 1 and net is None and not se3 and os.environ.get("GSD_TRAIN_STEP", "1") != "0":
         from gsd_amd.train_step import FusedTrainStep
@@ -455,6 +504,7 @@ def main():
         # train.py:323-332 + :529, lambda_dssim = 0.2: the offset-norm term is 0 (and skipped) when nothing moves
         # the means (configurations 2, 4, 5); in the SE(3) mode (1, 3) it is the moved distance's mean norm
         loss = training_loss(out["render"], target, out["means3D_offset"], 0.2)
+        last_loss[0] = loss.detach()   # for --dump-outputs (no device work)
         if FUSED_STEP:
             # backward + Adam: at N = 1 every gradient is final inside the preprocess backward, which applies
             # the Adam step there (FusedAdam.step_in_backward, gsd_adam_epilogue); with N > 1 the gradients
@@ -547,7 +597,7 @@ def main():
     # data parallel: the replicated parameters must still be bit-identical on every rank after the timed steps
     # (every rank applies the same summed gradients): a bit-pattern checksum of the parameter slab, min == max
     replicas = None
-    if world > 1:
+    if world > 1 and args.full:
         with torch.no_grad():
             ck = opt.param_slab.view(torch.int32).to(torch.int64).sum().reshape(1)
             lo, hi = ck.clone(), ck.clone()
@@ -559,6 +609,30 @@ def main():
                 dist.all_reduce(lo, op=dist.ReduceOp.MIN)
                 dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             replicas = bool(int(lo.item()) == int(hi.item()))
+    if args.dump_outputs:
+        # The arrays two builds are compared by.  The render backward sums its gradients with float atomics, and Adam
+        # (eps 1e-15) turns the sign of a cancelling sum into a whole +-lr move, so a trajectory of many steps differs
+        # between two runs of one build by far more than rounding (1e-2 in the image after 25 steps).  What is written
+        # is therefore one more call of the timed path, untimed, from the state the first timed step started from (the
+        # restored initial parameters and optimizer state): its inputs are identical in every run.  Written: what the
+        # call hands back (image, radii, dL/dmeans2D, num_rendered, loss) and, for every trained parameter, the first
+        # Adam moment it left (0.1 x the gradient it applied: continuous in the gradient, where the parameter itself
+        # is p0 - lr sign(g)).  Every rank takes the step (it may hold collectives); rank 0 writes its view.
+        restore()
+        out = step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            vs = out["viewspace_grad"] if "viewspace_grad" in out else getattr(out["viewspace_points"], "grad", None)
+            arrays = {"render": out["render"], "radii": out["radii"], "viewspace_grad": vs,
+                      "num_rendered": int(gsdC.last_forward.get("num_rendered", 0)),
+                      "loss": fused_step.loss() if fused_step is not None else last_loss[0]}
+            names = ["_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"]
+            if se3 and pc._twist is not None:
+                names.append("_twist")
+            arrays.update({"exp_avg" + n: opt.moments(getattr(pc, n))[0] for n in names})
+            if net is not None:
+                arrays["exp_avg_offset_model"] = torch.cat([opt.moments(p)[0].reshape(-1) for p in net.parameters()])
+            dump_outputs(args.dump_outputs, arrays)
     # GSD_BENCH_STEP_ONLY=1 (profiling: rocprofv3 --pmc over this script): only the warmup and the timed steps, so
     # every launch the counters see is a bench step's; the line then carries no fwd+bwd or per-kernel figures
     if os.environ.get("GSD_BENCH_STEP_ONLY") == "1":
@@ -566,6 +640,35 @@ def main():
             print(json.dumps({"metric": METRIC, "value": round(world * args.steps / elapsed, 3), "unit": "views/s",
                               "n_gpus": world, "steps": args.steps, "ms_per_step": round(1000.0 * elapsed / args.steps, 4),
                               "step_only": True}), flush=True)
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    workload = (f"cfg{args.config}: {P} Gaussians, SH deg {D}, {W}x{H}, 1 view/GPU; "
+                + ("per-Gaussian SE(3) deform (fused exp-map) + " if se3 else "")
+                + ("MLP live: DirectTemporalNeRF offsets (iteration 5000) + " if net is not None else "")
+                + "render fwd + 0.8 L1 + 0.2 (1 - SSIM)"
+                + (" + 0.1 mean |offset|" if net is not None else "") + " + bwd"
+                + (" + d_se3" if se3 else "")
+                + (" + MLP bwd" if net is not None else "")
+                + " + densification statistics + RCCL all-reduce of per-Gaussian grads + Adam"
+                + (" (incl. the MLP's group)" if net is not None else "")
+                + (f"; densify_and_prune every {densify_every} steps" if densify_every else ""))
+    step_path = "gsd_train_step (one native call)" if fused_step is not None else "drop-in API"
+    if not args.full:
+        # the plain run: the headline figure only; every other measurement is behind --full
+        if rank == 0:
+            print(json.dumps({
+                "metric": METRIC, "value": round(world * args.steps / elapsed, 3), "unit": "views/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(1000.0 * elapsed / args.steps, 4), "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": {"workload": workload, "P": P, "width": W, "height": H, "sh_degree": D,
+                           "views_per_step": world, "parallelism": f"dp{world}",
+                           "num_rendered_timed_first": K_start, "num_rendered_timed_last": K_end,
+                           "densify_interval": densify_every or None, "deform_mlp": net is not None,
+                           "P_timed_last": P_end},
+                "step_path": step_path, "full": False}), flush=True)
         if dist.is_initialized():
             dist.barrier()
             dist.destroy_process_group()
@@ -699,17 +802,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "config": {"workload": f"cfg{args.config}: {P} Gaussians, SH deg {D}, {W}x{H}, 1 view/GPU; "
-                                   + ("per-Gaussian SE(3) deform (fused exp-map) + " if se3 else "")
-                                   + ("MLP live: DirectTemporalNeRF offsets (iteration 5000) + " if net is not None
-                                      else "")
-                                   + "render fwd + 0.8 L1 + 0.2 (1 - SSIM)"
-                                   + (" + 0.1 mean |offset|" if net is not None else "") + " + bwd"
-                                   + (" + d_se3" if se3 else "")
-                                   + (" + MLP bwd" if net is not None else "")
-                                   + " + densification statistics + RCCL all-reduce of per-Gaussian grads + Adam"
-                                   + (" (incl. the MLP's group)" if net is not None else "")
-                                   + (f"; densify_and_prune every {densify_every} steps" if densify_every else ""),
+            "config": {"workload": workload,
                        "P": P, "width": W, "height": H, "sh_degree": D, "views_per_step": world,
                        "parallelism": f"dp{world}", "visible": V, "num_rendered": K,
                        "num_rendered_timed_first": K_start, "num_rendered_timed_last": K_end,
@@ -723,7 +816,8 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
         }
-        res["step_path"] = "gsd_train_step (one native call)" if fused_step is not None else "drop-in API"
+        res["step_path"] = step_path
+        res["full"] = True
         if dropin is not None:
             res["dropin_api_step"] = dropin
         if exchange is not None:

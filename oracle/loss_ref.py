@@ -3,8 +3,8 @@
 float32 torch restatement of the training loss, utils/loss_utils.py:17-63 and train.py:529:
 l1_loss = mean|x - y| (:17-18); gaussian window (:23-25), create_window (:27-31), _ssim (:43-63) with
 grouped conv2d, zero padding window_size // 2, C1 = 0.01^2, C2 = 0.03^2; loss = (1 - l) L1 + l (1 - SSIM).
-Pinned against tests/golden/loss.npz (values produced by the reference module itself).  Device-agnostic:
-runs on CPU here and on the GPU box as the fp32 autograd reference for gsd_amd.loss.
+Pinned against tests/golden/loss.npz (values produced by the reference module itself).  Takes tensors of any
+device as the fp32 autograd reference for gsd_amd.loss; the SSIM windows are always convolved on the CPU (see ssim).
 """
 from __future__ import annotations
 
@@ -31,6 +31,12 @@ def create_window(window_size, channel, device):
 
 
 def ssim(x, y, window_size=11):
+    """The five window convolutions run on the CPU whatever the inputs' device (the copies are differentiable, so
+    the gradient arrives on x's device): on a HIP device torch hands conv2d to MIOpen, which has no tuned or
+    precompiled kernels for gfx950 and builds them at run time into a cache in the user's home directory -- a
+    reference must not depend on that directory's state, nor on a compiler running inside the test process."""
+    dev = x.device
+    x, y = x.cpu(), y.cpu()
     channel = x.size(-3)
     w = create_window(window_size, channel, x.device).type_as(x)
     pad = window_size // 2
@@ -42,7 +48,7 @@ def ssim(x, y, window_size=11):
     s12 = F.conv2d(x * y, w, padding=pad, groups=channel) - mu1_mu2
     C1, C2 = 0.01 ** 2, 0.03 ** 2
     m = ((2 * mu1_mu2 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2))
-    return m.mean()
+    return m.mean().to(dev)
 
 
 def l1_ssim_loss(x, y, lambda_dssim=0.2):

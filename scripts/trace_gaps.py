@@ -2,9 +2,9 @@
 """Idle gaps between consecutive kernels of a rocprofv3 kernel trace (one bench step, the last complete one
 between two launches of the step's last kernel: the SH backward with the fused Adam epilogue, or the
 separate Adam kernel of the unfused and the data-parallel steps): prints each kernel's start offset, duration and the gap before it.
-    python scripts/trace_gaps.py gpurun_out/prof/bench_kernel_trace.csv [step index]
-bench.py's trace holds the warmup steps, the timed steps, then the kernels_ms pass (hipEvents around every launch,
-which add ~10 us before each kernel): pass the index of a timed step (e.g. 10 for `--warmup 5`) to see those."""
+    python scripts/trace_gaps.py <trace dir>/bench_kernel_trace.csv [step index]
+bench.py's trace holds the warmup steps, the timed steps, then (with --full) the kernels_ms pass (hipEvents around
+every launch, which add ~10 us before each kernel): pass the index of a timed step (e.g. 10 for `--warmup 5`) to see those."""
 import csv
 import sys
 

@@ -46,6 +46,32 @@ def test_check_ranks_and_launcher_argv():
     assert argv[-4:] == ["--gpus", "4", "--steps", "7"] and argv[-5].endswith("bench.py")
 
 
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """--dump-outputs: float32 files (a number: one float64); an array below its cap whole and in shape, one above
+    it as the same sorted sample on every call; None skipped; the 64-MB limit enforced."""
+    import numpy as np
+    import torch
+
+    import bench
+    big = torch.arange(bench.DUMP_ARRAY_ELEMS + 1000, dtype=torch.float32)
+    arrays = {"render": torch.arange(24, dtype=torch.float64).reshape(3, 2, 4), "radii": torch.tensor([3, 0, 7]),
+              "big": big, "num_rendered": 2 ** 24 + 1, "absent": None}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["big", "num_rendered", "radii", "render"]
+    assert got["render"].dtype == np.float32 and got["render"].shape == (3, 2, 4)
+    assert np.array_equal(got["render"].ravel(), np.arange(24)) and np.array_equal(got["radii"], [3, 0, 7])
+    assert got["num_rendered"].dtype == np.float64 and got["num_rendered"][0] == 2 ** 24 + 1
+    assert got["big"].dtype == np.float32 and got["big"].shape == (bench.DUMP_ARRAY_ELEMS,)
+    assert np.all(np.diff(got["big"]) >= 0) and got["big"][-1] <= big[-1]   # values are their own indices
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    # the worst case the bench writes: the image at its cap and a dozen capped arrays
+    assert 4 * (bench.DUMP_IMAGE_ELEMS + 12 * bench.DUMP_ARRAY_ELEMS) + 64 <= bench.DUMP_MAX_BYTES <= 64 * 1000 * 1000
+    with pytest.raises(RuntimeError, match="--dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big[:bench.DUMP_ARRAY_ELEMS] for i in range(22)})
+
+
 def test_roofline_uses_only_the_same_workloads_pmc(tmp_path, monkeypatch):
     import bench
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))

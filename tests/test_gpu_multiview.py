@@ -214,8 +214,8 @@ def test_bench_gpus_2_spawns_two_ranks(sh_views):
     env = dict(os.environ, GSD_DIST_BACKEND="gloo", GSD_SH_VIEWS=sh_views)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "2", "--steps",
-                        "3", "--warmup", "1", "--cpu-baseline", "off"], env=env, capture_output=True, text=True,
-                       timeout=240)
+                        "3", "--warmup", "1", "--full", "--cpu-baseline", "off"], env=env, capture_output=True,
+                       text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
